@@ -10,13 +10,19 @@ subtask, so a partition is any split of each window): every workload is ONE fixe
 r-th contiguous 1/N of every window. Strong scaling: value = (edges of the whole stream) * K / max-over-ranks time.
 
 N=1 default workload: C4, Kronecker scale 26 (64M vertices, 2^30 edges, 8 GiB of edges), one merge window — the
-config the north-star target is quoted on; it fits one GPU. Extra legs on rank 0 at N=1 (outside the timed
-region of the headline value): host-fed rate (pinned host memory + H2D), C2 R-MAT s20 rotating over 4 distinct
-batches (537 MB: no batch is still in the 256 MiB Infinity Cache when it is folded again), CPU baseline (the C
-restatement of the reference topology, oracle/cc_oracle.c) at T = 1, the box's CPU quota and nproc threads.
-Parity: the final labels' digest vs tests/golden/stream_digests.json (oracle digests computed on the CPU).
+config the north-star target is quoted on; it fits one GPU.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]  (N>1 under torch.distributed.run, one rank per GPU).
+A plain run does only what the headline value needs: set up, warm up, time the K steps, print the result line.
+--dump-outputs DIR also writes what the last timed step computed (the canonical labels) as .npy files.
+--full adds everything else, after the timed region: instrumented steps for the per-kernel and roofline figures (and
+the merge timing at N > 1), parity (the final labels' digest vs tests/golden/stream_digests.json, oracle digests
+computed on the CPU), and on rank 0 at N=1 the extra legs: every other config, BipartitenessCheck, host-fed rate
+(pinned host memory + H2D), C2 R-MAT s20 rotating over 4 distinct batches (537 MB: no batch is still in the 256 MiB
+Infinity Cache when it is folded again), CPU baseline (the C restatement of the reference topology,
+oracle/cc_oracle.c) at T = 1, the box's CPU quota and nproc threads.
+
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+(N>1 under torch.distributed.run, one rank per GPU).
 """
 from __future__ import annotations
 
@@ -75,15 +81,52 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="c4_kron26")
     ap.add_argument("--window-edges", type=int, default=0, help="edges per merge window (0 = config default)")
-    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="target CPU-baseline work per thread count (0 = skip)")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the host-fed and rotating-C2 legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the instrumented steps (per-kernel and roofline figures), "
+                         "parity, the extra legs and the CPU baseline; off: the headline measurement alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0,
+                    help="with --full: target CPU-baseline work per thread count (0 = skip)")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity check")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra legs")
     ap.add_argument("--tune", default="", help="fold-pipeline knobs k=v,... (gcc_forest_tune; speed only)")
     ap.add_argument("--phase-timing", choices=["timed", "after", "off"], default="after",
-                    help="per-kernel dispatch events in the timed steps, in extra steps after them, or not at all")
+                    help="per-kernel dispatch events in the timed steps, in extra steps after them (with --full "
+                         "only), or not at all")
     ap.add_argument("--step-marker", action="store_true",
                     help="launch gcc_step_mark_kernel once per step (rocprofv3 runs count steps by it)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_MAX_IDS = 1 << 21  # ids per dumped array (float64: 16 MiB each), a seeded sample of a larger forest
+DUMP_SEED = 0x6E11
+
+
+def dump_outputs(path, labels):
+    """What a caller of the timed path receives after the last timed step: the canonical labels (labels_device: the
+    component's smallest id per seen vertex, 0xFFFFFFFF for an id never seen) as float64 (u32 is exact in it).
+    labels.npy holds every id's label, or those of a fixed seeded sample of ids (labels_index.npy, ascending) when
+    the forest has more than DUMP_MAX_IDS ids; summary.npy = [ids, seen, components, digest >> 32, digest & 2^32-1]
+    over ALL ids (label_digest), so that two builds can be compared on the whole output as well."""
+    import numpy as np
+
+    V = labels.size
+    if V > DUMP_MAX_IDS:
+        index = np.unique(np.random.default_rng(DUMP_SEED).integers(0, V, size=DUMP_MAX_IDS))
+    else:
+        index = np.arange(V)
+    seen = int(np.count_nonzero(labels != 0xFFFFFFFF))
+    comps = int(np.count_nonzero(labels == np.arange(V, dtype=np.uint32)))
+    digest = label_digest(labels)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "labels.npy"), labels[index].astype(np.float64))
+    np.save(os.path.join(path, "labels_index.npy"), index.astype(np.float64))
+    np.save(os.path.join(path, "summary.npy"),
+            np.array([V, seen, comps, digest >> 32, digest & 0xFFFFFFFF], dtype=np.float64))
 
 
 def golden_digests():
@@ -715,8 +758,9 @@ def main():
     for _ in range(args.warmup):
         step(False)
     # "timed": every kernel of the timed steps carries its own dispatch start/stop events (hipExtLaunchKernel, no
-    # extra packets); "after": the timed steps run bare and min(steps, 5) instrumented steps follow them
+    # extra packets); "after" (--full only): the timed steps run bare and min(steps, 5) instrumented steps follow them
     timed_inst = args.phase_timing == "timed"
+    after_inst = args.full and args.phase_timing == "after"
     forest.ds.enable_timing(1 if timed_inst else 0)
     forest.ds.fold_profile()  # drain the warmup log
     torch.cuda.synchronize()
@@ -735,8 +779,12 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # the last timed step's summary, read back before anything else runs on the forest
+    labels = forest.ds.labels() if args.full or args.dump_outputs else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, labels)
     inst_steps = args.steps if timed_inst else 0
-    if args.phase_timing == "after":
+    if after_inst:
         inst_steps = min(args.steps, 5)
         forest.ds.enable_timing(1)
         for _ in range(inst_steps):
@@ -744,20 +792,22 @@ def main():
         torch.cuda.synchronize()
     log = forest.ds.fold_profile()
     forest.ds.enable_timing(0)
-    kstats, phases, spans = kernel_stats(log, V, inst_steps)
-    timing_note = ("hipExtLaunchKernel dispatch events on the forest's stream, every timed step" if timed_inst
-                   else f"hipExtLaunchKernel dispatch events, {inst_steps} steps after the timed region")
-    roofline = make_roofline(kstats, phases, spans, inst_steps, args.workload, timing_note, host_fold_s)
+    roofline = None
+    if args.full or timed_inst:
+        kstats, phases, spans = kernel_stats(log, V, inst_steps)
+        timing_note = ("hipExtLaunchKernel dispatch events on the forest's stream, every timed step" if timed_inst
+                       else f"hipExtLaunchKernel dispatch events, {inst_steps} steps after the timed region")
+        roofline = make_roofline(kstats, phases, spans, inst_steps, args.workload, timing_note, host_fold_s)
 
     merge_ms = [a.elapsed_time(b) for a, b in merge_events]
-    labels = forest.ds.labels()
-    seen = int(np.count_nonzero(labels != 0xFFFFFFFF))
-    comps = int(np.count_nonzero(labels == np.arange(V, dtype=np.uint32)))
-    digests = golden_digests()
-    parity = None
+    seen = comps = parity = None
+    digests = golden_digests() if args.full else {}
+    if args.full:
+        seen = int(np.count_nonzero(labels != 0xFFFFFFFF))
+        comps = int(np.count_nonzero(labels == np.arange(V, dtype=np.uint32)))
     if not args.no_parity and args.workload in digests:  # any window size: the final partition is the stream's
         parity = "bit-exact" if label_digest(labels) == int(digests[args.workload]["digest"]) else "MISMATCH"
-    if dist:  # every rank holds the global partition after the merge: all must agree with the fixture
+    if dist and args.full:  # every rank holds the global partition after the merge: all must agree with the fixture
         ok = torch.tensor([0 if parity == "MISMATCH" else 1], dtype=torch.int32, device=f"cuda:{local}")
         dist.all_reduce(ok, op=dist.ReduceOp.MIN)
         if parity is not None and int(ok.item()) == 0:
@@ -805,7 +855,9 @@ def main():
                            source="DESIGN.md §6 (per-rank folds and merge kernels measured on one GPU; all_gather modelled)")
                       if PREDICTED.get(args.workload, {}).get(world) else None),
         "parity": parity,
-        "summary": {"seen": seen, "components": comps},
+        "full": args.full,
+        "summary": {"seen": seen, "components": comps} if args.full else None,
+        "outputs": args.dump_outputs,
         "merge": ({"ms_per_window": sum(merge_ms) / len(merge_ms), "windows_per_step": n_windows,
                    "ms_per_step": sum(merge_ms) / max(1, inst_steps),
                    "message_bytes": group.last.get("bytes"),
@@ -817,7 +869,7 @@ def main():
                    "timing": "torch events around gcc_forest_group_merge on the forest's stream, instrumented steps"}
                   if group is not None and merge_ms else None),
     }
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         forest.ds.close()
         try:
             result["configs"] = config_legs(local, args.steps, args.warmup, digests, tune,
@@ -844,7 +896,7 @@ def main():
                 result["c2_rotating"] = c2_rotating_leg(local, args.steps, args.warmup, digests, tune)
             except Exception as e:
                 result["c2_rotating"] = {"error": repr(e)}
-    if world == 1 and args.cpu_seconds > 0:
+    if args.full and world == 1 and args.cpu_seconds > 0:
         result["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
     print(json.dumps(result))
     if dist:

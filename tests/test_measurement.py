@@ -30,6 +30,46 @@ def test_profile_record_picks_the_newest_session():
     assert rec["file"] == f"profiles/{newest}"
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """--full and --dump-outputs are off unless asked for: a plain run is the headline measurement alone."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    args = bench.parse()
+    assert (args.full, args.dump_outputs, args.steps, args.warmup) == (False, None, 3, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert (args.full, args.dump_outputs) == (True, "d")
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """A small forest is dumped whole; a larger one as the same seeded sample of ids on every call, with the digest and
+    the counts of ALL labels beside it; every array float64 (exact for u32) and the files 64 MB at the most."""
+    import numpy as np
+
+    lab = np.array([0, 0, 2, 0xFFFFFFFF, 2, 5], dtype=np.uint32)
+    bench.dump_outputs(str(tmp_path / "small"), lab)
+    got = np.load(tmp_path / "small" / "labels.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, lab.astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "small" / "labels_index.npy"), np.arange(6))
+    d = bench.label_digest(lab)
+    assert np.load(tmp_path / "small" / "summary.npy").tolist() == [6, 5, 3, d >> 32, d & 0xFFFFFFFF]
+
+    V = bench.DUMP_MAX_IDS + 12345
+    big = (np.arange(V, dtype=np.uint32) // 7) * 7
+    big[::11] = 0xFFFFFFFF
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), big)
+    idx = np.load(tmp_path / "a" / "labels_index.npy")
+    assert idx.dtype == np.float64 and 0 < idx.size <= bench.DUMP_MAX_IDS and np.all(np.diff(idx) > 0) and idx[-1] < V
+    assert np.array_equal(np.load(tmp_path / "a" / "labels.npy"), big[idx.astype(np.int64)].astype(np.float64))
+    total = 0
+    for f in ("labels.npy", "labels_index.npy", "summary.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+        total += os.path.getsize(tmp_path / "a" / f)
+    assert total <= 64e6
+    d = bench.label_digest(big)
+    assert np.load(tmp_path / "a" / "summary.npy")[3:].tolist() == [d >> 32, d & 0xFFFFFFFF]
+
+
 def _write_counters(path, rows):
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "w", newline="") as f:

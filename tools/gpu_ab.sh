@@ -14,7 +14,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_bucket.py tests/test_gpu_wi
 trc=$?
 tail -3 "$OUT/tests.log"
 if [ $trc -ne 0 ]; then grep -E "FAILED|Error" "$OUT/tests.log" | head; exit $trc; fi
-B="python -u bench.py --steps 20 --warmup 3 --cpu-seconds 0 --no-extras"
+B="python -u bench.py --full --steps 20 --warmup 3 --cpu-seconds 0 --no-extras"
 for v in new_p1_1 old new_p1_2 new_p1_0 new_p1_1b; do
   echo "== $v"
   case $v in

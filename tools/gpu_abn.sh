@@ -10,7 +10,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
-B="python -u bench.py --steps 20 --warmup 3 --cpu-seconds 0 --no-extras $ARGS"
+B="python -u bench.py --full --steps 20 --warmup 3 --cpu-seconds 0 --no-extras $ARGS"
 for r in 1 2; do
   for nl in "$@"; do
     name=${nl%%=*}

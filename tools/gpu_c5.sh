@@ -16,7 +16,7 @@ timeout -k 10 700 python -u -m pytest tests/test_gpu_windows.py tests/test_gpu_p
 trc=$?
 tail -3 "$OUT/tests.log"
 if [ $trc -ne 0 ]; then grep -E "FAILED|Error|inc_check" "$OUT/tests.log" | head -20; exit $trc; fi
-B="python -u bench.py --steps 20 --warmup 3 --cpu-seconds 0 --no-extras"
+B="python -u bench.py --full --steps 20 --warmup 3 --cpu-seconds 0 --no-extras"
 run() {  # name, lib ("" = in-tree), bench args...
   local name=$1 lib=$2; shift 2
   echo "== $name"

@@ -9,7 +9,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-CMD="python3 $ROOT/bench.py --workload $WL --steps 2 --warmup 1 --cpu-seconds 0 --no-extras --no-parity"
+CMD="python3 $ROOT/bench.py --full --workload $WL --steps 2 --warmup 1 --cpu-seconds 0 --no-extras --no-parity"
 echo "== trace" && timeout -k 10 120 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- $CMD > "$OUT/trace.json" 2> "$OUT/trace.err" && \
 echo "== sq a" && timeout -s KILL 120 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE --output-format csv -d "$OUT/sqa" -o run -- $CMD > "$OUT/sqa.json" 2> "$OUT/sqa.err" && \
 echo "== sq b" && timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_WAVES SQ_INST_LEVEL_VMEM SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS --output-format csv -d "$OUT/sqb" -o run -- $CMD > "$OUT/sqb.json" 2> "$OUT/sqb.err" && \

@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
-B="python -u bench.py --steps 20 --warmup 3 --cpu-seconds 0 --no-extras"
+B="python -u bench.py --full --steps 20 --warmup 3 --cpu-seconds 0 --no-extras"
 run() {  # name, bench args...
   local name=$1; shift
   echo "== $name"

@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
-B="python -u bench.py --steps 20 --warmup 3 --cpu-seconds 0 --no-extras"
+B="python -u bench.py --full --steps 20 --warmup 3 --cpu-seconds 0 --no-extras"
 echo "== c4 p2_per 8" && timeout -k 10 240 $B > "$OUT/c4_p8.json" 2> "$OUT/c4_p8.err" && \
 echo "== c4 p2_per 12" && timeout -k 10 240 $B --tune bucket_p2_per=12 > "$OUT/c4_p12.json" 2> "$OUT/c4_p12.err" && \
 echo "== c4 p2_per 8 again" && timeout -k 10 240 $B > "$OUT/c4_p8b.json" 2> "$OUT/c4_p8b.err" && \

@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
-B="python -u bench.py --steps 20 --warmup 3 --cpu-seconds 0 --no-extras"
+B="python -u bench.py --full --steps 20 --warmup 3 --cpu-seconds 0 --no-extras"
 for p1 in 1 2 0; do
   echo "== c4 bucket_p1=$p1"
   timeout -k 10 240 $B --tune bucket_p1=$p1 > "$OUT/c4_p1_$p1.json" 2> "$OUT/c4_p1_$p1.err" || exit $?

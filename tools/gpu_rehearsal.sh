@@ -8,7 +8,7 @@
 set -o pipefail
 O=${O:-gpurun_out/rehearsal}; mkdir -p $O
 R="python -m torch.distributed.run --nnodes=1 --master-addr 127.0.0.1"
-B="bench.py --steps 5 --warmup 2 --cpu-seconds 0 --no-extras"
+B="bench.py --full --steps 5 --warmup 2 --cpu-seconds 0 --no-extras"
 export GELLY_SHARE_GPU=1 GELLY_DIST_BACKEND=gloo GELLY_RCCL_LIB=$PWD/tests/cpp/build/libshm_rccl.so
 timeout -k 10 300 $R --nproc-per-node 2 --master-port 29511 $B --gpus 2 > $O/c4_2.json 2> $O/c4_2.err && echo c4x2 ok && \
 timeout -k 10 300 $R --nproc-per-node 4 --master-port 29512 $B --gpus 4 > $O/c4_4.json 2> $O/c4_4.err && echo c4x4 ok && \

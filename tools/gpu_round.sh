@@ -18,10 +18,10 @@ if [ $trc -gt 1 ]; then echo "tests ended with status $trc: stopping"; exit $trc
 echo "== smoke" && \
 timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 && tail -1 "$OUT/smoke.log" && \
 echo "== bench" && \
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err" && \
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err" && \
 echo "== rocprof" && \
 (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-    python3 "$ROOT/bench.py" --steps 10 --warmup 2 --cpu-seconds 0 --no-extras > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err")
+    python3 "$ROOT/bench.py" --full --steps 10 --warmup 2 --cpu-seconds 0 --no-extras > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err")
 rc=$?
 python3 -c "
 import json

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
 smi() { timeout -k 5 30 rocm-smi --showclocks --showpower --showtemp 2>/dev/null | grep -E "sclk|mclk|fclk|Power|Temperature \(Sensor (edge|junction|memory)" | tr -s ' ' | head -12; }
-B="python -u bench.py --steps 20 --warmup 3 --cpu-seconds 0 --no-extras"
+B="python -u bench.py --full --steps 20 --warmup 3 --cpu-seconds 0 --no-extras"
 # MODES: one GELLY_CONTIG value per run (default: five runs of the default build)
 MODES=${MODES:-"1 1 1 1 1"}
 r=0

@@ -51,7 +51,7 @@ def main():
         "algorithmic_bytes_per_launch": per * edges,
         "l2_hit_rate": hit / (hit + miss),
         "source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE / TCC_HIT_sum,TCC_MISS_sum (separate passes), "
-                  f"bench.py --steps 5; bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 per launch",
+                  f"bench.py --full --steps 5; bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 per launch",
     }
     rec["all_kernels"] = {  # every kernel of the run: HBM bytes per launch (same correction)
         k: {"launches": len(f[k]), "hbm_bytes_per_launch": (2 * sum(f[k]) / len(f[k]) + (sum(w[k]) / len(w[k]) if w.get(k) else 0)) * 1024}
